@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- CV fits/sec of the nFolds x alpha x lambda grid on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--workload config2|config3|config4|config5]
+    python bench.py --gpus N --steps K --warmup W [--workload config2|config3|config4|config5] [--full]
+                    [--dump-outputs DIR]
 
 Workloads (BASELINE.json `configs`):
   config2 (default, the configuration the metric is quoted on): synthetic Gaussian n=1000, p=10000, nFolds=5,
@@ -20,6 +21,10 @@ BuildGrid, AssignToFolds, context creation (H2D, hipMalloc) and the first run.
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); the cost-sorted cell list is dealt
 round-robin to the ranks (total work fixed -> "strong" scaling), one all-gather per step.  Started without a
 launcher (`python bench.py --gpus N`, WORLD_SIZE unset) it starts the N ranks itself.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes time of its own beyond
+that: the CPU leg (`cpu_baseline`, the oracle on a sample of the same grid, about a minute and a half for config2).
+--dump-outputs DIR writes the last timed step's results as DIR/<name>.npy (float64), see dump_outputs().
 
 Prints ONE JSON line on rank 0.
 """
@@ -153,6 +158,31 @@ def cpu_leg(np, X, y, folds, nF, alpha, lam, prior, epis, budget_s, heavy):
                       % (fits, [round(float(v), 4) for v in a_pick], l_idx.tolist(), len(L), done, nF, cpu, thr, wall)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, state, alpha, lam, np):
+    """What the timed path handed its caller in the last step, as float64 .npy files: the per-cell fold scores and status
+    words (CrossValidate's Results.Detail), the grid, the summary table sorted alpha then lambda (Results.Summary) and the
+    optimum (alpha*, lambda*, cv.error).  Event counters are instrumentation, not results, and are not written.  Above
+    DUMP_MAX_BYTES every per-cell array keeps the same fixed, seeded sample of its rows (their indices in sample_cells.npy)."""
+    a_s, l_s, se, cv, idx = state["summary"]
+    per_cell = {"fold_err": state["fold_err"], "status": state["status"], "grid_alpha": alpha, "grid_lambda": lam,
+                "summary_alpha": a_s, "summary_lambda": l_s, "summary_se": se, "summary_cv_error": cv}
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in per_cell.items()}
+    n_cells = len(alpha)
+    row_bytes = sum(v.nbytes for v in out.values()) // max(n_cells, 1)
+    keep = (DUMP_MAX_BYTES - 4096) // (row_bytes + 8)
+    if n_cells > keep:
+        rows = np.sort(np.random.default_rng(20251004).choice(n_cells, size=keep, replace=False))
+        out = {k: v[rows] for k, v in out.items()}
+        out["sample_cells"] = rows.astype(np.float64)
+    out["optimum"] = np.array(state["best"], dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -164,9 +194,15 @@ def main():
     ap.add_argument("--nfolds", type=int, default=0)
     ap.add_argument("--nalpha", type=int, default=0)
     ap.add_argument("--nlambda", type=int, default=0)
-    ap.add_argument("--cpu-baseline", type=int, default=1, help="0 disables the CPU leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU leg (cpu_baseline)")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: 0 disables the CPU leg")
     ap.add_argument("--cpu-budget-s", type=float, default=45.0, help="wall-clock budget of the CPU leg (checked between folds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -239,7 +275,8 @@ def main():
             fold_err = np.empty((n_cells, nF)); status = np.empty((n_cells, nF), dtype=np.int32)
             fold_err[mine] = err; status[mine] = st
         a_s, l_s, se, cv, idx = summarise_cv(alpha, lam, fold_err, nF, prior)
-        state.update(cnt=cnt, status=status, best=(float(a_s[idx]), float(l_s[idx]), float(cv[idx])),
+        state.update(cnt=cnt, status=status, fold_err=fold_err, summary=(a_s, l_s, se, cv, idx),
+                     best=(float(a_s[idx]), float(l_s[idx]), float(cv[idx])),
                      timing=ctx.last_timing(), launch=ctx.launch_info())
 
     def fence():
@@ -357,8 +394,10 @@ def main():
             "roofline": roof,
         }
     ctx.close()
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, state, alpha, lam, np)
 
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if rank == 0 and world == 1 and args.full and args.cpu_baseline:
         result["cpu_baseline"] = cpu_leg(np, X, y, folds, nF, alpha, lam, prior, epis, args.cpu_budget_s,
                                          heavy=(n * K > 4e7))
     if rank == 0:

@@ -1,7 +1,8 @@
 """bench.py's output contract on a GPU box, at a rehearsal size that finishes in seconds: exactly one JSON
-line on stdout with the keys the driver reads, the roofline and cpu_baseline objects, and the same
-(alpha*, lambda*, cv.error) whether the per-cell errors are kept local or go through the RCCL all-gather
-(PAREBEN_BENCH_FORCE_DIST=1: a one-rank process group on the one GPU, the N > 1 code path)."""
+line on stdout with the keys the driver reads, the roofline object, the cpu_baseline object under --full (and not
+without it), the same (alpha*, lambda*, cv.error) whether the per-cell errors are kept local or go through the RCCL
+all-gather (PAREBEN_BENCH_FORCE_DIST=1: a one-rank process group on the one GPU, the N > 1 code path), and the
+--dump-outputs files of the last timed step."""
 import json
 import os
 import subprocess
@@ -27,7 +28,7 @@ def _run(extra_args, extra_env=None):
 
 
 def test_bench_json_contract_and_collective_path():
-    r = _run(["--cpu-budget-s", "1"])
+    r = _run(["--full", "--cpu-budget-s", "1"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in r, k
@@ -48,11 +49,35 @@ def test_bench_json_contract_and_collective_path():
     assert fk["mfma"]["executed_mfma_flops_per_launch"] > 0 and fk["hbm"]["algorithmic_bytes_per_launch"] > 0
     cb = r["cpu_baseline"]
     assert cb["kind"] == "port" and cb["unit"] == "fits/s" and cb["value"] > 0 and cb["cores"] >= 1 and "sample" in cb
-    d = _run(["--cpu-baseline", "0"], {"PAREBEN_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29533",
-                                        "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
+    d = _run(["--full", "--cpu-baseline", "0"], {"PAREBEN_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1",
+                                                 "MASTER_PORT": "29533", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
     for k in ("alpha_opt", "lambda_opt", "cv_error", "aborted_fits"):
         assert d["config"][k] == r["config"][k], k                  # bit-identical through the all-gather
     assert "cpu_baseline" not in d
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) leaves out the CPU leg; --steps sets the timed steps; --dump-outputs writes the last
+    step's results as float64 .npy files, equal to the result line's optimum and identical through the all-gather."""
+    import numpy as np
+    a, b = tmp_path / "local", tmp_path / "gathered"
+    r = _run(["--dump-outputs", str(a)])
+    assert "cpu_baseline" not in r and r["steps"] == 2 and r["ms_per_step"] > 0
+    d = _run(["--dump-outputs", str(b)], {"PAREBEN_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29535",
+                                          "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
+    names = sorted(f.name for f in a.iterdir())
+    assert names == sorted(f.name for f in b.iterdir())
+    assert names == sorted(n + ".npy" for n in ("fold_err", "status", "grid_alpha", "grid_lambda", "summary_alpha",
+                                                  "summary_lambda", "summary_se", "summary_cv_error", "optimum"))
+    E = np.load(a / "fold_err.npy")
+    assert E.dtype == np.float64 and E.shape == (4 * 6, 3) and np.all(np.isfinite(E))
+    S = np.load(a / "status.npy")
+    assert S.shape == E.shape and np.all(S == np.round(S)) and np.all((S.astype(np.int32) & 8) == 0)
+    opt = np.load(a / "optimum.npy")
+    assert opt.tolist() == [r["config"]["alpha_opt"], r["config"]["lambda_opt"], r["config"]["cv_error"]]
+    for n in names:
+        assert np.array_equal(np.load(a / n), np.load(b / n)), n     # bit-identical through the all-gather
+    assert d["config"]["cv_error"] == r["config"]["cv_error"]
 
 
 def test_bench_gpus_flag_is_honoured():
